@@ -1,11 +1,19 @@
-"""Benchmark: rrLU GFLOP/s at (m, n, r) = (8192, 8192, 256) on MI355X (BASELINE.json metric), plus
-Pi-rows/s of the batch-evaluation kernel and the TCI2 sweep wall time of config 1.
+"""Benchmark: rrLU GFLOP/s at (m, n, r) = (8192, 8192, 256) on MI355X (BASELINE.json metric); with
+--full also Pi-rows/s of the batch-evaluation kernel, the TCI2 sweep wall times of the BASELINE
+configs, the CPU baselines and the parity check against them.
 
 A "step" is one rrlu(A; maxrank=r) on a synthetic U[0,1) Float64 matrix resident in HBM
 (copy into the work buffer included, as rrlu = rrlu!(copy(A)), matrixlu.jl:462).
 value = sum_{k=1..r} 2(m-k)(n-k) flops x ranks / max-over-ranks time.
 
-  python bench.py [--gpus N --steps K --warmup W] [--m M --n N --r R] [--no-extras] [--no-cpu]
+  python bench.py [--gpus N --steps K --warmup W] [--m M --n N --r R] [--dump-outputs DIR]
+                  [--full [--no-extras] [--no-cpu]]
+A plain run sets up, warms up, times the K steps and prints the result line (with the roofline of
+the passes that HIP events sampled inside those steps). --full adds everything that takes runs of
+its own: the stream-read / stream-copy calibration, the extras (Pi assembly, TCI2 configs, dense
+MFMA kernels, sharded paths; --no-extras leaves them out), and the CPU baselines with the bitwise
+parity check of the benchmarked factorisation (--no-cpu leaves them out).
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy.
 N > 1: launched by torch.distributed.run, one process per GPU; each rank factorises its own
 matrix (weak scaling, no data-path collective; DESIGN.md "Multi-GPU").
 """
@@ -96,8 +104,14 @@ def main():
     ap.add_argument("--m", type=int, default=8192)
     ap.add_argument("--n", type=int, default=8192)
     ap.add_argument("--r", type=int, default=256)
-    ap.add_argument("--no-extras", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: stream calibration, extras, "
+                         "CPU baselines and the parity check against them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (npivot, lasterror, pivoterrors: what "
+                         "rrlu_inplace_device returns on the timed path) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave the extras out")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--cpu-pivots", type=int, default=256)
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="diagnostic: no HIP events in the timed region (no roofline line)")
@@ -112,6 +126,8 @@ def main():
     ap.add_argument("--no-shadow", action="store_true",
                     help="exact fp64 read-only passes instead of the certified narrow-shadow search")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # the result is ONE JSON line on stdout: native libraries' banners (RCCL prints its version
     # block to fd 1 when the sharded extras create a communicator) go to stderr instead
     global _OUT_FD
@@ -166,10 +182,16 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        np_, err, _, _, _ = step()
+        np_, err, _, _, pe_ = step()
     barrier()
     dt = time.perf_counter() - t0
     assert np_ == min(r, m, n), np_
+    if args.dump_outputs:
+        # the timed path (want_perms=False) hands its caller npivot, lu.error and the np + 1 pivot
+        # errors; the work matrix is scratch (stale trailing values) and L / U stay in the context
+        dump_outputs(args.dump_outputs, rank, world, {"npivot": np.array([np_], np.float64),
+                                                      "lasterror": np.array([err], np.float64),
+                                                      "pivoterrors": np.asarray(pe_, np.float64)})
     wb_ms, wb_launches = ctx.kernel_stats(0)
     # read-only passes: per-pass launches (family 2, pass 0 excluded: family 43) and the persistent
     # shadow-epoch launches (41 first shadow epoch, 42 later ones; units = the passes they ran)
@@ -190,10 +212,12 @@ def main():
         if pn:
             by_pending_ext[P] = round(pm / pn, 5)
     ctx.set_timing(False)
-    # the benchmarked factorisation once more with permutations and pivot errors, for the parity
-    # check against the CPU runs on the same matrix (rank 0 factorises the seed-0 matrix)
-    npd, _, rpd, cpd, ped = T.rrlu_inplace_device(W, maxrank=r, want_perms=True, src=A)
-    dev_res = (npd, rpd[:m].copy(), cpd[:n].copy(), ped.copy())
+    dev_res = None
+    if args.full:
+        # the benchmarked factorisation once more with permutations and pivot errors, for the parity
+        # check against the CPU runs on the same matrix (rank 0 factorises the seed-0 matrix)
+        npd, _, rpd, cpd, ped = T.rrlu_inplace_device(W, maxrank=r, want_perms=True, src=A)
+        dev_res = (npd, rpd[:m].copy(), cpd[:n].copy(), ped.copy())
     if dist is not None:
         import torch
         t = torch.tensor([dt], dtype=torch.float64)
@@ -289,21 +313,22 @@ def main():
     # the same fraction from the committed rocprofv3 kernel trace of this configuration: every
     # read-only pass's device time (no event overhead, pass 0 apart) over the schedule's pass count
     out["roofline"].update(trace_frac(m, n, r, nb, args.epochs, shadow, sh_bytes))
-    # roofline calibration on the same buffers: 16-B stream read and stream copy, best grid
-    import ctypes as C
-    nel = A.ld * n
-    best_r = best_c = 0.0
-    for grid in (256, 512, 1024, 2048):
-        ms_r, ms_c = C.c_double(), C.c_double()
-        ctx.check(ctx.lib.tci_diag_stream_d(ctx.h, A.ptr, W.ptr, nel, 5, grid, C.byref(ms_r), C.byref(ms_c)))
-        best_r = max(best_r, 8.0 * nel / (ms_r.value * 1e-3) / 1e9)
-        best_c = max(best_c, 16.0 * nel / (ms_c.value * 1e-3) / 1e9)
-    out["roofline"]["measured_stream_read_GBps"] = round(best_r, 1)
-    out["roofline"]["measured_stream_copy_GBps"] = round(best_c, 1)
+    if args.full:
+        # roofline calibration on the same buffers: 16-B stream read and stream copy, best grid
+        import ctypes as C
+        nel = A.ld * n
+        best_r = best_c = 0.0
+        for grid in (256, 512, 1024, 2048):
+            ms_r, ms_c = C.c_double(), C.c_double()
+            ctx.check(ctx.lib.tci_diag_stream_d(ctx.h, A.ptr, W.ptr, nel, 5, grid, C.byref(ms_r), C.byref(ms_c)))
+            best_r = max(best_r, 8.0 * nel / (ms_r.value * 1e-3) / 1e9)
+            best_c = max(best_c, 16.0 * nel / (ms_c.value * 1e-3) / 1e9)
+        out["roofline"]["measured_stream_read_GBps"] = round(best_r, 1)
+        out["roofline"]["measured_stream_copy_GBps"] = round(best_c, 1)
     A.free()
     W.free()
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         sh = sharded_pi(T, ctx, dist, world, rank)
         shq = sharded_pi(T, ctx, dist, world, rank, "quantics_osc")
         try:  # a failure of the multi-GPU extras must not cost the headline line
@@ -333,7 +358,7 @@ def main():
                                                           "ms": g["ms"]}
             out["scaling_lines"] = lines
     parity_ok = True
-    if rank == 0 and not args.no_cpu and world == 1:
+    if args.full and rank == 0 and not args.no_cpu and world == 1:
         base, cpu_res = cpu_baseline(m, n, r, args.cpu_pivots)
         out["cpu_baseline"] = base
         out["parity"] = parity_vs_cpu(dev_res, cpu_res, r)
@@ -346,6 +371,15 @@ def main():
     if not parity_ok:
         sys.stderr.write("bench: device rrLU differs from the CPU oracle on the benchmarked matrix\n")
         sys.exit(3)
+
+
+def dump_outputs(directory, rank, world, arrays):
+    """DIR/<name>.npy per output of the last timed step (ranks above 0 of a multi-GPU run, each of
+    which factorises its own matrix, write DIR/<name>_rank<k>.npy)."""
+    os.makedirs(directory, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 and rank else ""
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), arr)
 
 
 PMC_SUMMARY = os.path.join(ROOT, "profiles", "r06_i1_pmc_summary.json")
