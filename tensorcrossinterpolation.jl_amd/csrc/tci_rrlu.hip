@@ -1365,6 +1365,16 @@ static_assert(kMfBlk == 4, "a lane's 16 loaded rows are 4 blocks of 4");
 // y_k per staged column in LDS (examinations read the pending y's from Y) so that the 64-slot
 // fragments fit.
 constexpr int kMfMaxP = 15;
+// Shadow chunks a wave keeps in flight while it streams. With the 8-bit
+// shadow a chunk is one 16-B load per lane, so two of them cover half the bytes the fp16 loop had
+// outstanding -- but the loop is bound by the instructions it issues per chunk, not by its loads:
+// 3 and 4 measured 1.3 and 3.3 us slower per pass at 8192^2 (spills, a longer seed), so the
+// default stays 2 (make variant ... VFLAGS=-DTCI_MF_INFLIGHT=3 for A/B runs).
+#ifndef TCI_MF_INFLIGHT
+#define TCI_MF_INFLIGHT 2
+#endif
+constexpr int kMfInflight = TCI_MF_INFLIGHT;
+static_assert(kMfInflight >= 2 && kMfInflight <= 8, "the seed consumes two buffers; each costs 4-8 VGPRs");
 constexpr int kMfExCap = 128;                         // deferred examinations per wave
 #ifndef TCI_EXB
 #define TCI_EXB 4
@@ -1381,6 +1391,13 @@ struct MfGeom {
     // shadow epoch: EXT) only y_k -- the examinations then read the pending y's from Y
     static constexpr bool ymem = deep || EXT;
     static constexpr int YS = ymem ? 1 : P;
+};
+// Per-instance streaming depth: the two-K-step instances (P > 10) already spill and stay at 2.
+// EXT and RF are not used yet: they are the hook for specialising an instance that cannot take a
+// depth above 2 without scratch in its loop (at depth 3 the non-EXT refreshes P = 8, 10).
+template <int P, bool EXT, bool RF>
+struct MfDepth {
+    static constexpr int D = P > 10 ? 2 : kMfInflight;
 };
 
 // v - x_0 y_0 - x_1 y_1 - ... (cnt terms, in order; separate multiply and subtract, the
@@ -1704,12 +1721,14 @@ __device__ __forceinline__ int pass_mf_body(const PassK& g, const SelArgs& sel, 
     const int prow = tx - kP2StageCols;  // this thread's tile row (row threads)
     const int rrow = tb + (prow >= 0 ? prow : 0);
     const int rpl = rowpos_of(min(rrow, m - 1));
-    ShVec va[kShVecs], vb[kShVecs];
+    constexpr int D = MfDepth<P, EXT, RF>::D;  // chunk buffers in flight
+    ShVec vbuf[D][kShVecs];
     const int gc0 = ntc > 0 ? min(G, ntc) * cb : 0;
     const int nch0 = (gc0 + 15) / 16;
     // unconditional (no columns: chunk 0 of an empty group reads column n - 1, never used)
-    load_chunk(0, gc0, max(min(rep, nch0 - 1), 0), va);
-    load_chunk(0, gc0, max(min(rep + kMfReps, nch0 - 1), 0), vb);
+    // (the first two buffers only: more prefetches held across the EXT prologue spill)
+    load_chunk(0, gc0, max(min(rep, nch0 - 1), 0), vbuf[0]);
+    load_chunk(0, gc0, max(min(rep + kMfReps, nch0 - 1), 0), vbuf[1]);
     // (the map values are tested where they are first needed, after the pivot-dependent loads have
     // gone out: tested here, their wait held those loads back by a round trip)
     // EXT: the pivot-independent side of this thread's chain (row thread: X[s][row]; stager:
@@ -1837,6 +1856,10 @@ __device__ __forceinline__ int pass_mf_body(const PassK& g, const SelArgs& sel, 
         if (stager) yk0 = pend_chain<COH>(a0, pre, g.Y + jj, ldy, upl, PE - 1);
     }
     PPROF(1);
+    // the other buffers' first chunks: the prologue's chain registers are dead, the staging and its
+    // barrier are still ahead
+#pragma unroll
+    for (int i = 2; i < D; ++i) load_chunk(0, gc0, max(min(rep + i * kMfReps, nch0 - 1), 0), vbuf[i]);
     bool act = false;
 #pragma unroll
     for (int b = 0; b < kMfBlk; ++b) act |= sb + 16 * (lcol >> 2) + 4 * b + (lcol & 3) < m && rpa[b] > k;
@@ -1871,7 +1894,8 @@ __device__ __forceinline__ int pass_mf_body(const PassK& g, const SelArgs& sel, 
                 // -128 comes from the MFMA's constant slot
                 const uint32_t d = __builtin_bit_cast(u32x4v, v[0])[b];
                 acc = f4v{(float)(d & 0xFFu), (float)((d >> 8) & 0xFFu), (float)((d >> 16) & 0xFFu), (float)(d >> 24)};
-                if (!rload) acc = f4v{128.0f, 128.0f, 128.0f, 128.0f};  // rows past the shadow: W = 0
+                // (rows past the shadow: masked after the MFMA, one select per block instead of one per
+                // element -- their x's are 0, so the MFMA adds only the offset slot to what was loaded)
             } else {
                 const h8v hv = __builtin_bit_cast(h8v, v[(b >> 1) % kShVecs]);
                 const int o = 4 * (b & 1);
@@ -1880,8 +1904,13 @@ __device__ __forceinline__ int pass_mf_body(const PassK& g, const SelArgs& sel, 
             }
 #pragma unroll
             for (int u = 0; u < KSt; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[b][u], bf[u], acc, 0, 0, 0);
-            mbs[b] = __builtin_fmaxf(__builtin_fmaxf(fabsf(acc[0]), fabsf(acc[1])),
-                                     __builtin_fmaxf(fabsf(acc[2]), fabsf(acc[3])));
+            // (a chain, not a tree: the compiler folds it into max3 + max with |.| source modifiers; the
+            // tree cost two more instructions per block)
+            mbs[b] = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(fabsf(acc[0]), fabsf(acc[1])), fabsf(acc[2])),
+                                     fabsf(acc[3]));
+            if constexpr (kShU8) {
+                if (!rload) mbs[b] = 0.0f;  // rows past the shadow: W = 0
+            }
             c = __builtin_fmaxf(c, mbs[b]);
             if constexpr (RF) {  // rows rl + 4 b + t: the new epoch's shadow, 0 off the trailing block
                 if constexpr (kShU8) {
@@ -1983,6 +2012,11 @@ __device__ __forceinline__ int pass_mf_body(const PassK& g, const SelArgs& sel, 
     // append the lane's blocks whose maximum reaches bound (chunk h); flushes first if needed
     auto append = [&](int g0, int h, const float (&mbs)[kMfBlk], float bound) {
         const unsigned lc = (unsigned)(h * 16 + lcol);
+        // Nearly every chunk appends nothing: one test of the lane's largest block (no block can pass
+        // where that one fails: the sum below is monotone) instead of four tests and ballots
+        const float mx = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(mbs[0], mbs[1]), mbs[2]), mbs[3]);
+        static_assert(kMfBlk == 4, "mx covers every block");
+        if (__ballot(mx >= 0.0f && mx + eps >= bound) == 0) return;
 #pragma unroll
         for (int b = 0; b < kMfBlk; ++b) {
             const bool f = mbs[b] >= 0.0f && mbs[b] + eps >= bound;
@@ -2020,10 +2054,10 @@ __device__ __forceinline__ int pass_mf_body(const PassK& g, const SelArgs& sel, 
                 cpst = jst >= 0 ? ep->lcol[lcol_of(g0, tx)] : -1;
             else
                 cpst = (jst >= 0 && jst < n) ? colpos[jst] : -1;
-            // unconditional (an inactive wave loads two chunks it never reads): loads skipped on
+            // unconditional (an inactive wave loads chunks it never reads): loads skipped on
             // some paths into the loop would make its head wait for every load in flight
-            load_chunk(g0, gcols, min(rep, nch - 1), va);
-            load_chunk(g0, gcols, min(rep + kMfReps, nch - 1), vb);
+#pragma unroll
+            for (int i = 0; i < D; ++i) load_chunk(g0, gcols, min(rep + i * kMfReps, nch - 1), vbuf[i]);
             __syncthreads();
         }
         [[maybe_unused]] double ykg = yk0;  // EXT: this group's y_k chain (whole stager waves)
@@ -2089,7 +2123,7 @@ __device__ __forceinline__ int pass_mf_body(const PassK& g, const SelArgs& sel, 
             }
         }
         if (g0 == 0) PPROF(7);
-        if (tx < kMfSlices) L.cnt[tx] = 2 * kMfReps;
+        if (tx < kMfSlices) L.cnt[tx] = D * kMfReps;
         if (g0 == 0 && tx == 0) L.tau = 0u;
         __syncthreads();
         if (g0 == 0) {
@@ -2107,24 +2141,49 @@ __device__ __forceinline__ int pass_mf_body(const PassK& g, const SelArgs& sel, 
             if (lane == 0) h = atomicAdd(&L.cnt[slice], 1);
             return __builtin_amdgcn_readfirstlane(h);
         };
-        int h0 = rep, h1 = rep + kMfReps;
-        float mb0[kMfBlk], mb1[kMfBlk];
+        // buffer i holds chunk h[i]; pre-assigned h_i = rep + i kMfReps, the counter starts past them
+        int h[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) h[i] = rep + i * kMfReps;
+        // One buffer's turn: consume it, grab the next index and reissue the buffer's load at once,
+        // then test / append. The load is issued unconditionally: a fixed number of loads per turn
+        // lets each chunk's wait count the other buffers' loads (a skipped one would force a wait
+        // for every outstanding load). A chunk past the group (only in a wave's last trip, or a
+        // pre-assigned one of a short group) skips its approx() (no loads) in the first-epoch
+        // passes: at small sizes (where those are the only read-only passes) a wave streams one or
+        // two chunks, and the dead turns would multiply its work. A refresh keeps it, inert, for its
+        // fixed count of stores, and the EXT passes too (skipping it there changes their register
+        // allocation: prologue spills).
+        auto turn = [&](int i, bool first) {
+            const int e = h[i];
+            float mbs[kMfBlk];
+            float c = -1.0f;
+            const bool on = first || RF || EXT || e < nch;
+            if (on) c = approx(e, gcols, vbuf[i], mbs);
+            h[i] = grab();
+            load_chunk(g0, gcols, min(h[i], nch - 1), vbuf[i]);
+            if (on) {  // (inert past the group: c and mbs are -1)
+                test(c);
+                append(g0, e, mbs, tau - tau * margin);
+            }
+        };
         if (g0 == 0) {
             // seed: the first two chunks of every wave set the workgroup's bound first
             float c0 = -1.0f, c1 = -1.0f;
-            const int e0 = h0, e1 = h1;
+            float mb0[kMfBlk], mb1[kMfBlk];
+            const int e0 = h[0], e1 = h[1];
 #pragma unroll
             for (int b = 0; b < kMfBlk; ++b) mb0[b] = mb1[b] = -1.0f;
             // approx() of a chunk past the group is inert (-1, no stores). The grabs and loads run
             // in inactive waves too (a slice's waves share its rows, so they are all inactive and
             // take nothing from an active one): loads skipped on the way into the loop below would
             // make its head wait for every load in flight.
-            if (wact) c0 = approx(h0, gcols, va, mb0);
-            h0 = grab();
-            load_chunk(g0, gcols, min(h0, nch - 1), va);
-            if (wact && (RF || EXT || h1 < nch)) c1 = approx(h1, gcols, vb, mb1);
-            h1 = grab();
-            load_chunk(g0, gcols, min(h1, nch - 1), vb);
+            if (wact) c0 = approx(e0, gcols, vbuf[0], mb0);
+            h[0] = grab();
+            load_chunk(g0, gcols, min(h[0], nch - 1), vbuf[0]);
+            if (wact && (RF || EXT || e1 < nch)) c1 = approx(e1, gcols, vbuf[1], mb1);
+            h[1] = grab();
+            load_chunk(g0, gcols, min(h[1], nch - 1), vbuf[1]);
             if (wact) {
                 float lb = fmaxf(fmaxf(c0, c1) - eps, 0.0f);
 #pragma unroll
@@ -2137,37 +2196,18 @@ __device__ __forceinline__ int pass_mf_body(const PassK& g, const SelArgs& sel, 
             const float bound = tau - tau * margin;
             if (e0 < nch) append(g0, e0, mb0, bound);
             if (e1 < nch) append(g0, e1, mb1, bound);
+            // the other buffers' pre-assigned chunks, against the seeded bound
+#pragma unroll
+            for (int i = 2; i < D; ++i) turn(i, false);
         } else if (!wact) {
             continue;
         }
-        // h0's values in va, h1's in vb; every grab returns a larger index than both, so h1 >= nch
-        // only in the last trip. Both halves issue their loads unconditionally: a fixed number of
-        // loads per trip lets each chunk's wait count the other chunk's loads (a skipped half
-        // would force a wait for every outstanding load). The last trip's h1 >= nch skips its
-        // approx() (no loads) in the first-epoch passes: at small sizes (where those are the only
-        // read-only passes) a wave streams one or two chunks, and the dead half would double its
-        // work. A refresh keeps it, inert, for its fixed count of stores, and the EXT passes too
-        // (skipping it there changes their register allocation: prologue spills).
-        while (h0 < nch) {
-            {
-                const float c = approx(h0, gcols, va, mb0);
-                const int e = h0;
-                h0 = grab();
-                load_chunk(g0, gcols, min(h0, nch - 1), va);
-                test(c);
-                append(g0, e, mb0, tau - tau * margin);
-            }
-            {
-                const int e = h1;
-                float c = -1.0f;
-                if (RF || EXT || e < nch) c = approx(e, gcols, vb, mb1);
-                h1 = grab();
-                load_chunk(g0, gcols, min(h1, nch - 1), vb);
-                if (RF || EXT || e < nch) {  // (inert past the group: c and mb1 are -1)
-                    test(c);
-                    append(g0, e, mb1, tau - tau * margin);
-                }
-            }
+        // Every grab returns a larger index than all before it and the pre-assigned ones, so
+        // h[0] < h[1] < ... here and after every trip: h[0] >= nch means every buffer is past the
+        // group, and h[i] >= nch for i > 0 only in the last trip.
+        while (h[0] < nch) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) turn(i, i == 0);
         }
         // the latest bound of the workgroup prunes the list
         tau = fmaxf(tau, __uint_as_float(__hip_atomic_load(&L.tau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)));
